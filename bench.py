@@ -8,9 +8,14 @@ byte range at multiples of 2^34 (cuts fall inside records); every rank scans its
 ranks exchange 7 words of carry, re-run only the emit step with the true carry, and all-reduce the
 counts (and histograms) over RCCL.  value = total bytes of all ranks / max-over-ranks time.
 
-Prints ONE JSON line (rank 0).  Extra keys: roofline (k_index, the dominant kernel, measured with
-HIP events on the launch stream inside the timed region), cpu_baseline (the oracle timed on the
-host cores, rank 0, N = 1 only), stats (the histogram pass on the same buffer, configs[2]).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps and prints the line
+(roofline: k_index, the dominant kernel, measured with HIP events on the launch stream inside the
+timed region).  --full adds everything else the benchmark measures or checks, in runs of their own:
+other input allocations (best_allocation), roofline traffic from rocprofv3 counters, the read
+ceiling, stats (the histogram pass on the same buffer, configs[2]), kilobase reads, the streamed
+leg (configs[3]), cpu_baseline (the oracle timed on the host cores, rank 0, N = 1 only), host_api,
+the one-rank RCCL protocol check and the sharded host-streamed leg (configs[4]).
+--dump-outputs DIR writes what the last timed step computed (record offsets, summary, carry) as .npy.
 """
 import argparse
 import json
@@ -66,10 +71,10 @@ def main():
     ap.add_argument("--slot-mib", type=int, default=256, help="ring slot size of the streamed modes")
     ap.add_argument("--producer-threads", type=int, default=0,
                     help="threads that fill a ring slot from pageable host memory (0: 1, the reference's one reader thread, AND 8)")
-    ap.add_argument("--no-stream", action="store_true", help="skip the configs[3] leg of the default run")
-    ap.add_argument("--no-long-reads", action="store_true", help="skip the kilobase-read histogram leg of the default run")
+    ap.add_argument("--no-stream", action="store_true", help="skip the configs[3] leg of a --full run")
+    ap.add_argument("--no-long-reads", action="store_true", help="skip the kilobase-read histogram leg of a --full run")
     ap.add_argument("--default-stream-gib", type=float, default=256.0,
-                    help="size of the configs[3] leg of the default run (its stated size: 256 GiB, ~5 s at the link's rate; the "
+                    help="size of the configs[3] leg of a --full run (its stated size: 256 GiB, ~5 s at the link's rate; the "
                          "one-thread producer run stops at 8 GiB)")
     ap.add_argument("--numa-pin", choices=["auto", "require", "off"], default="auto",
                     help="streamed legs: run on (and first-touch the pinned ring from) the NUMA node of the GPU.  auto: best effort, "
@@ -83,11 +88,20 @@ def main():
                          "torch.distributed.  auto: abi when the backend is nccl (or there is one rank), torch under gloo (the one-GPU "
                          "functional mode: RCCL does not put two ranks on one device)")
     ap.add_argument("--default-shard-stream-gib", type=float, default=128.0,
-                    help="GiB PER RANK of the configs[4] leg every default run carries (key `sharded_stream`); 128 gives 1 TiB at 8 ranks")
-    ap.add_argument("--no-shard-stream", action="store_true", help="skip the configs[4] leg of the default run")
+                    help="GiB PER RANK of the configs[4] leg every --full run carries (key `sharded_stream`); 128 gives 1 TiB at 8 ranks")
+    ap.add_argument("--no-shard-stream", action="store_true", help="skip the configs[4] leg of a --full run")
     ap.add_argument("--no-host-api", action="store_true", help="skip the timing of the drop-in host API (host/bin/fastq_count) on the configs[0] file")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other measurement and check (input allocation candidates, "
+                         "rocprofv3 traffic, read ceiling, histograms, long reads, streamed legs, CPU baseline, host API, RCCL "
+                         "protocol check, configs[4]); a plain run measures the headline figure only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (record offsets: all, or a fixed seeded sample of at most 2^21; "
+                         "the summary; the carry) as DIR/<name>.npy in float64; bench_outputs/ is git-ignored")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` with no launcher around it: be the launcher (one rank per GPU, the contract's command line)
@@ -163,6 +177,8 @@ def main():
     nbytes = hi - lo
 
     ctx = pkg.Ctx(dev.index, stream=torch.cuda.current_stream().cuda_stream)
+    # (one rank: the timed steps use no collective, but the communicator is made in every run all the same — its device memory
+    # is allocated before the input's, and where the input lands decides the byte scan's speed: DESIGN.md 4b)
     coll = Coll(pkg, torch, dist, ctx, dev, world, rank, backend, via)
     rccl["via"] = coll.via_text
     if os.environ.get("FQH_BENCH_PLACE_TRIES"):
@@ -180,8 +196,8 @@ def main():
     # caller who owns ONE buffer gets: the timed steps run on the FIRST allocation.  What other allocations would have
     # given is measured as well and reported next to it (config.input_placement; N = 1 only): the harness allocates two more
     # inputs, lets the context settle on each (ten untimed phase-free byte scans) and, if one of them is faster than the first,
-    # runs the same warm-up and timed steps on it.  FQH_BENCH_INPUT_CANDIDATES=1 skips that.
-    n_cand = int(os.environ.get("FQH_BENCH_INPUT_CANDIDATES", "3")) if (world == 1 and nbytes >= (2 << 30) and not args.pmc_child and args.stream_gib == 0) else 1
+    # runs the same warm-up and timed steps on it (--full only).  FQH_BENCH_INPUT_CANDIDATES=1 skips that.
+    n_cand = int(os.environ.get("FQH_BENCH_INPUT_CANDIDATES", "3")) if (args.full and world == 1 and nbytes >= (2 << 30) and not args.pmc_child and args.stream_gib == 0) else 1
     cands, cand_ms = [], []
     for k in range(max(1, n_cand)):
         st_k = torch.empty(LEAD + nbytes + 16, dtype=torch.uint8, device=dev)
@@ -235,6 +251,7 @@ def main():
     counts = torch.zeros(2, dtype=torch.int64, device=dev)
     index_ms = []
     host_steps = [0]
+    last = {}   # (the carry the last step handed back, for --dump-outputs)
 
     def step_host():
         # 1) shard-local byte scan (phase-free), 2) carry exchange, 3) emit with the true carry
@@ -254,6 +271,7 @@ def main():
                                       [int(x) for x in rows[r][3:7]])
         ctx.rescan_launch(is_last, carry, rec_start.data_ptr(), cap)
         s, c, st = ctx.scan_finish()
+        last["carry"] = c
         h_counts[0] = s.n_records
         h_counts[1] = 1 if s.parse_status != pkg.OK else 0
         counts.copy_(h_counts, non_blocking=True)
@@ -264,6 +282,7 @@ def main():
         if world == 1:
             s, c, st = ctx.scan(cur["buf"].data_ptr(), nbytes, True, None, rec_start.data_ptr(), cap)
             index_ms.append(ctx.timing().index_ms)
+            last["carry"] = c
             return s
         if os.environ.get("FQH_BENCH_HOST_PROTOCOL") == "1":
             return step_host()
@@ -280,6 +299,7 @@ def main():
                 print("rank %d: E_AGAIN, gathered words %s" % (rank, all_words.cpu().numpy().reshape(world, W).tolist()), file=sys.stderr, flush=True)
             return step_host()
         index_ms.append(ctx.timing().index_ms)
+        last["carry"] = c
         return s
 
     if args.stream_gib > 0:
@@ -314,6 +334,8 @@ def main():
         return dt_, s_, settle
 
     dt, s, settle = timed_steps()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, np, torch, rec_start, s, last["carry"], "" if world == 1 else "_rank%d" % rank)
     index_ms_first = list(index_ms)
     best_allocation = None
     if alt_store is not None and inject < 0:
@@ -362,7 +384,7 @@ def main():
         emit_line({"pmc_child": True, "kernel_ms": round(k_ms, 4)})
         ctx.read_ceiling(buf.data_ptr(), nbytes)
         return
-    if world == 1 and args.pmc_traffic == "auto":
+    if args.full and world == 1 and args.pmc_traffic == "auto":
         live = pmc_traffic(nbytes)
         if live:
             traffic, traffic_source = live["hbm_bytes_per_launch"], live["source"]
@@ -437,6 +459,7 @@ def main():
         t = ctx.timing()
         out["stage_ms"] = {"index": round(t.index_ms, 4), "prefix": round(t.prefix_ms, 4),
                            "emit": round(t.emit_ms, 4), "total": round(t.total_ms, 4)}
+    if rank == 0 and world == 1 and args.full:
         rc_ms = [ctx.read_ceiling(buf.data_ptr(), nbytes)[1] for _ in range(6)]   # (a ceiling is the fastest launch, not an average)
         out["read_ceiling_gbs"] = round(nbytes / 1e9 / (min(rc_ms) / 1e3), 1)
         out["read_ceiling_ms"] = {"min": round(min(rc_ms), 4), "max": round(max(rc_ms), 4), "launches": len(rc_ms)}
@@ -590,7 +613,7 @@ def main():
                 d1 = time.perf_counter() - t1
             out["cpu_baseline"]["stats_parallel_gbs"] = round(sample / 1e9 / d1, 3)
             out["cpu_baseline"]["stats_parallel_threads"] = nthr
-    if world == 1 and coll.comm:
+    if args.full and world == 1 and coll.comm:
         # the HBM-resident protocol once through the library's own RCCL binding with a communicator of this one rank (untimed):
         # words -> fqh_allgather -> fold + emit -> fqh_allreduce_u64, one host wait — what every step does at N > 1
         w1 = torch.zeros(W, dtype=torch.int64, device=dev)
@@ -601,8 +624,8 @@ def main():
         s1, _, _ = ctx.scan_finish()
         assert (s1.parse_status, int(s1.n_records)) == (pkg.OK, total_records) and counts.cpu().tolist() == [total_records, 0]
         out["rccl"]["protocol_check"] = "one HBM-resident sharded step (prescan, fqh_allgather, fold + emit, fqh_allreduce_u64) through a 1-rank fqh_comm: %d records" % total_records
-    if not args.no_shard_stream:
-        # configs[4] in every default line: the sharded, host-streamed leg at this world size next to the same
+    if args.full and not args.no_shard_stream:
+        # configs[4] in every --full line: the sharded, host-streamed leg at this world size next to the same
         # function at world size 1
         inj = int(os.environ.get("FQH_BENCH_INJECT_STREAM", "-1"))   # (tests only)
         if inj >= 0:
@@ -651,6 +674,29 @@ def main():
     ctx.close()
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_SAMPLE = 1 << 21   # record offsets --dump-outputs writes at most (16 MiB of float64, as much again for their record numbers)
+
+
+def dump_outputs(d, np, torch, rec_start, s, carry, suffix=""):
+    """--dump-outputs DIR: what the last timed step handed its caller, as float64 .npy (offsets < 2^53 are exact).
+    rec_start + rec_start_index: the record offsets and their record numbers — all of them up to DUMP_SAMPLE records, else the
+    first and last DUMP_SAMPLE / 4 and a fixed seeded sample of the rest; summary: fqh_summary's fields in order (the reserved
+    word left out); carry: base_offset, nl_count, back[4]."""
+    os.makedirs(d, exist_ok=True)
+    n = min(int(s.n_records), rec_start.numel())
+    if n <= DUMP_SAMPLE:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        edge = DUMP_SAMPLE // 4
+        mid = np.random.default_rng(20261016).integers(edge, n - edge, DUMP_SAMPLE // 2)
+        idx = np.unique(np.concatenate([np.arange(edge), mid, np.arange(n - edge, n)]))
+    vals = rec_start[torch.from_numpy(idx).to(rec_start.device)].cpu().numpy()
+    summary = [getattr(s, f) for f, _ in s._fields_ if f != "reserved"]
+    for name, a in (("rec_start", vals), ("rec_start_index", idx), ("summary", summary),
+                    ("carry", [carry.base_offset, carry.nl_count] + list(carry.back))):
+        np.save(os.path.join(d, "%s%s.npy" % (name, suffix)), np.asarray(a, dtype=np.float64))
 
 
 def host_api_leg(path, nbytes, exp_hist):

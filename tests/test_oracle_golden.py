@@ -156,15 +156,23 @@ def test_synth_is_valid_fastq_and_counter_based(fqref):
 
 def test_kseq_cross_check_counts(fqref, tmp_path):
     """Secondary cross-check with the reference repo's own C comparator (examples/c/parse.c +
-    kseq.h, built by oracle/Makefile into oracle/_ref/): record COUNT on well-formed input."""
+    kseq.h): record COUNT on well-formed input.  Its counts are stored in tests/golden/kseq_counts.json;
+    where oracle/Makefile has built it into oracle/_ref/, its live output must equal them too."""
+    import hashlib
+    with open(os.path.join(HERE, "golden", "kseq_counts.json")) as f:
+        cases = json.load(f)["cases"]
+    inputs = {"correct": build_input(VECS["correct"]["input"]), "windows_lineend": build_input(VECS["windows_lineend"]["input"]),
+              "synth_5000_records": bytes(fqref.synth(0, 330 * 5000))}
+    assert sorted(c["name"] for c in cases) == sorted(inputs)
     exe = os.path.join(os.path.dirname(HERE), "oracle", "_ref", "kseq_count")
-    if not os.path.exists(exe):
-        pytest.skip("oracle/_ref/kseq_count not built (reference sources absent)")
-    for data in (build_input(VECS["correct"]["input"]), build_input(VECS["windows_lineend"]["input"]),
-                 bytes(fqref.synth(0, 330 * 5000))):
-        # kseq.h (2011) treats a short read() as EOF, so feed it a regular file, not a pipe
-        f = tmp_path / "in.fq"
-        f.write_bytes(data)
-        with open(f, "rb") as fh:
-            out = subprocess.run([exe], stdin=fh, capture_output=True, check=True).stdout
-        assert int(out.strip()) == fqref.count(data).n_records
+    for c in cases:
+        data = inputs[c["name"]]
+        assert (len(data), hashlib.sha256(data).hexdigest()) == (c["bytes"], c["sha256"]), c["name"]
+        assert fqref.count(data).n_records == c["kseq_count"], c["name"]
+        if os.path.exists(exe):
+            # kseq.h (2011) treats a short read() as EOF, so feed it a regular file, not a pipe
+            f = tmp_path / "in.fq"
+            f.write_bytes(data)
+            with open(f, "rb") as fh:
+                out = subprocess.run([exe], stdin=fh, capture_output=True, check=True).stdout
+            assert int(out.strip()) == c["kseq_count"], c["name"]

@@ -7,7 +7,7 @@ cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 OUT=gpurun_out/prof
 rm -rf $OUT; mkdir -p $OUT
-CMD="python bench.py --steps 5 --warmup 2 --no-cpu-baseline --pmc-traffic off --default-stream-gib 32 --default-shard-stream-gib 16"
+CMD="python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --pmc-traffic off --default-stream-gib 32 --default-shard-stream-gib 16"
 PMC_CMD="$CMD --no-stream --no-shard-stream"
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- $CMD > $OUT/trace.log 2>&1
 for pass in "FETCH_SIZE" "WRITE_SIZE" \

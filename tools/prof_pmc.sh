@@ -7,7 +7,7 @@ cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 OUT=gpurun_out/prof_pmc
 rm -rf $OUT; mkdir -p $OUT
-CMD=${FQH_PROF_CMD:-"python bench.py --steps 2 --warmup 1 --no-cpu-baseline"}
+CMD=${FQH_PROF_CMD:-"python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline"}
 i=0
 for pass in "$@"; do
   i=$((i+1))

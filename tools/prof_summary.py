@@ -36,7 +36,7 @@ if os.path.exists(log):
         bench = json.loads(lines[-1])
         with open(os.path.join(PROF, tag + "_bench_traced.json"), "w") as f:
             f.write(lines[-1])
-res = {"source": "tools/prof.sh (rocprofv3 --kernel-trace --stats, then --pmc passes) over: python bench.py --steps 5 --warmup 2 "
+res = {"source": "tools/prof.sh (rocprofv3 --kernel-trace --stats, then --pmc passes) over: python bench.py --full --steps 5 --warmup 2 "
                  "--no-cpu-baseline",
        "workload_bytes": bench["config"]["bytes_per_gpu"] if bench else None}
 for f in glob.glob(os.path.join(out, "trace", "**", "*kernel_stats.csv"), recursive=True):
