@@ -9,19 +9,24 @@ LIB_PATH = os.environ.get("FQH_LIB_PATH") or os.path.join(_HERE, "libfastq_hip.s
 
 __all__ = ["LIB_PATH", "lib", "Ctx", "Stream", "Comm", "COMM_ID_BYTES", "Chunk", "ShardResult", "READ_FN", "SHARD_STREAM_WORDS", "NO_ERROR_KEY", "shard_stream_outcome", "shard_failed_words", "shard_failure_key", "SHARD_EMPTY", "SHARD_PASS", "SHARD_DEFER", "STREAM_INDEX", "STREAM_STATS", "STREAM_TIMING", "StreamTimes", "Carry", "Summary", "Timing", "IdxRecord", "FqhError",
            "strerror", "carry_combine", "OK", "E_HEADER", "E_SEP", "E_LEN_MISMATCH", "E_TRUNCATED", "E_TOO_LONG",
-           "E_IO", "E_DEVICE", "E_ARG", "E_CAPACITY", "E_AGAIN", "SHARD_WORDS", "BUFSIZE", "NSCALARS", "OPT_FAST_PATH", "OPT_SINGLE_PASS", "OPT_PLACE_TRIES", "OPT_SPIN_WAIT", "OPT_REUSE_INDEX", "OPT_ADAPT_LINES", "OPT_OWN_STREAM_NONBLOCKING", "OPT_KEEP_RING", "STREAM_EXTERNAL", "MAP_FN", "EXPORTS"]
+           "E_IO", "E_DEVICE", "E_ARG", "E_CAPACITY", "E_AGAIN", "SHARD_WORDS", "BUFSIZE", "NSCALARS", "OPT_FAST_PATH", "OPT_SINGLE_PASS", "OPT_PLACE_TRIES", "OPT_SPIN_WAIT", "OPT_REUSE_INDEX", "OPT_ADAPT_LINES", "OPT_OWN_STREAM_NONBLOCKING", "OPT_KEEP_RING", "STREAM_EXTERNAL", "MAP_FN", "EXPORTS",
+           "ALIGN_MAX_QUERY", "FLAG_ADAPTER", "ADAPTER"]
 
 OK, E_HEADER, E_SEP, E_LEN_MISMATCH, E_TRUNCATED, E_TOO_LONG, E_IO, E_DEVICE, E_ARG, E_CAPACITY, E_AGAIN = range(11)
 SHARD_WORDS = 8
 BUFSIZE = 68 * 1024
 NSCALARS = 8
+ALIGN_MAX_QUERY = 64
+FLAG_ADAPTER = 4
+# examples/alignment_count.rs:8-10: the adapter the crate's alignment example counts hits against
+ADAPTER = b"AATGATACGGCGACCACCGAGATCTACACTCTTTCCCTACACGACGCTCTTCCGATCT"
 OPT_FAST_PATH, OPT_SINGLE_PASS, OPT_PLACE_TRIES, OPT_SPIN_WAIT, OPT_REUSE_INDEX, OPT_ADAPT_LINES, OPT_OWN_STREAM_NONBLOCKING, OPT_KEEP_RING = 1, 2, 3, 4, 5, 6, 7, 8
 
 # every symbol include/fastq_hip.h declares (tests check the library exports all of them)
 EXPORTS = [
     "fqh_create", "fqh_destroy", "fqh_strerror", "fqh_last_error", "fqh_abi_version",
     "fqh_set_stream", "fqh_set_bufsize", "fqh_set_option", "fqh_last_scan_fast", "fqh_last_stats_route", "fqh_placement", "fqh_line_buffers", "fqh_scan", "fqh_scan_launch", "fqh_scan_finish",
-    "fqh_shard_prescan", "fqh_shard_prescan_launch", "fqh_shard_rescan_launch", "fqh_shard_align", "fqh_stream_carry", "fqh_carry_combine", "fqh_rescan_launch", "fqh_invalidate", "fqh_index_records", "fqh_record_flags", "fqh_gather_records", "fqh_len_hist", "fqh_stats", "fqh_stats_launch", "fqh_stats_finish", "fqh_stats_launch_lead",
+    "fqh_shard_prescan", "fqh_shard_prescan_launch", "fqh_shard_rescan_launch", "fqh_shard_align", "fqh_stream_carry", "fqh_carry_combine", "fqh_rescan_launch", "fqh_invalidate", "fqh_index_records", "fqh_record_flags", "fqh_gather_records", "fqh_align_scores", "fqh_len_hist", "fqh_stats", "fqh_stats_launch", "fqh_stats_finish", "fqh_stats_launch_lead",
     "fqh_scan_stats", "fqh_scan_stats_launch", "fqh_scan_stats_finish", "fqh_last_timing",
     "fqh_stream_create", "fqh_stream_destroy", "fqh_stream_set_stats", "fqh_stream_acquire", "fqh_stream_submit",
     "fqh_stream_collect", "fqh_stream_release", "fqh_stream_timing", "fqh_stream_note_read", "fqh_comm_unique_id", "fqh_comm_create", "fqh_comm_destroy", "fqh_allgather",
@@ -146,6 +151,8 @@ def lib():
         L.fqh_stream_set_stats.argtypes = [vp, u32, vp, vp, vp]
         L.fqh_last_timing.argtypes = [vp, C.POINTER(Timing)]
         L.fqh_record_flags.argtypes = [vp, vp, u64, u64, vp, u64, vp]
+        L.fqh_align_scores.argtypes = [vp, vp, u64, u64, vp, u64, C.c_char_p, u32, C.c_int32, C.c_int32, C.c_int32,
+                                       C.c_int32, C.c_int32, vp, vp, vp, vp]
         L.fqh_len_hist.argtypes = [vp, vp, vp, C.c_uint32, vp]
         L.fqh_gather_records.argtypes = [vp, vp, u64, u64, vp, u64, vp, C.c_uint8, C.c_uint8, vp, u64,
                                          C.POINTER(u64), C.POINTER(u64)]
@@ -347,6 +354,14 @@ class Ctx:
         if st not in (OK, E_CAPACITY):
             self._chk(st)
         return st, ns.value, nb.value
+
+    def align_scores(self, d_buf, length, d_index, n, query=ADAPTER, match=1, mismatch=0, gap_open=8, gap_extend=1,
+                     threshold=10, d_score=None, d_end=None, d_flags=None, d_count=None, base_offset=0):
+        """Smith-Waterman-Gotoh local alignment score of every record's seq() against `query` (bytes, host memory); the
+        defaults are the crate's alignment example (examples/alignment_count.rs).  Enqueued on the context's stream."""
+        query = bytes(query)
+        self._chk(self._L.fqh_align_scores(self._h, d_buf, length, base_offset, d_index, n, query, len(query), match,
+                                           mismatch, gap_open, gap_extend, threshold, d_score, d_end, d_flags, d_count))
 
     def stats_launch(self, d_buf, length, lmax, d_qual, d_base, d_scalars, is_final=True, carry=None):
         self._chk(self._L.fqh_stats_launch(self._h, d_buf, length, 1 if is_final else 0,

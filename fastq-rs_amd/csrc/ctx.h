@@ -42,6 +42,8 @@ void launch_record_flags(hipStream_t, const uint8_t *, uint64_t, uint64_t, const
 uint64_t gather_blocks(uint64_t n);
 void launch_gather(hipStream_t, const uint8_t *, uint64_t, uint64_t, const fqh_idx_record *, uint64_t, const uint8_t *, uint32_t,
                    uint32_t, unsigned long long *, unsigned long long *, unsigned long long *, uint8_t *, uint64_t);
+void launch_align(hipStream_t, const uint8_t *, uint64_t, const fqh_idx_record *, uint64_t, const uint8_t *, uint32_t, int32_t, int32_t,
+                  int32_t, int32_t, int32_t, int32_t *, uint32_t *, uint8_t *, unsigned long long *);
 void launch_synth(hipStream_t, uint8_t *, uint64_t, uint64_t, uint64_t);
 void launch_read_ceiling(hipStream_t, const uint8_t *, uint64_t, uint64_t *, int);
 }  // namespace fqh

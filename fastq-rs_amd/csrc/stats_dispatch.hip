@@ -491,4 +491,23 @@ fqh_status fqh_gather_records(fqh_ctx *ctx, const uint8_t *d_buf, uint64_t len, 
     return FQH_OK;
 }
 
+fqh_status fqh_align_scores(fqh_ctx *ctx, const uint8_t *d_buf, uint64_t len, uint64_t base_offset,
+                            const fqh_idx_record *d_index, uint64_t n, const uint8_t *query, uint32_t query_len,
+                            int32_t match, int32_t mismatch, int32_t gap_open, int32_t gap_extend, int32_t threshold,
+                            int32_t *d_score, uint32_t *d_end, uint8_t *d_flags, uint64_t *d_count) {
+    (void)len;  // the records' own lengths bound every read (and lead bytes lie in front of d_buf)
+    if (!ctx || !query || (n && (!d_buf || !d_index))) return FQH_E_ARG;
+    if (query_len < 1 || query_len > FQH_ALIGN_MAX_QUERY) return fail(ctx, FQH_E_ARG, "query_len must be 1..64");
+    if (match < 1 || match > 127 || mismatch < -127 || mismatch > match || gap_extend < 0 || gap_extend > gap_open ||
+        gap_open > 127)
+        return fail(ctx, FQH_E_ARG, "scores out of range (1 <= match <= 127, -127 <= mismatch <= match, "
+                                    "0 <= gap_extend <= gap_open <= 127)");
+    if (ctx->pending || ctx->stats_pending) return fail(ctx, FQH_E_ARG, "a launch is pending");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    launch_align(ctx->stream, d_buf, base_offset, d_index, n, query, query_len, match, mismatch, gap_open, gap_extend,
+                 threshold, d_score, d_end, d_flags, (unsigned long long *)d_count);
+    HIPCHK(ctx, hipGetLastError());
+    return FQH_OK;
+}
+
 }  // extern "C"

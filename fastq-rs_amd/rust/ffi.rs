@@ -69,6 +69,8 @@ pub const FQH_SHARD_DEFER: u32 = 0xFFFF_FFFD;  // ... of a byte range whose wind
 pub const FQH_OPT_KEEP_RING: c_int = 8;         // default 0: a destroyed ring's pinned slots are freed, not kept for the next ring
 pub const FQH_ABI_VERSION: c_int = 1;
 pub const FQH_NSCALARS: usize = 8;
+pub const FQH_ALIGN_MAX_QUERY: u32 = 64;  // longest query of fqh_align_scores
+pub const FQH_FLAG_ADAPTER: u8 = 4;       // d_flags bit set by fqh_align_scores (bits 0-1: fqh_record_flags)
 // fqh_status (the five parse errors carry the crate's own messages: fqh_strerror)
 pub const FQH_E_HEADER: c_int = 1;        // src/records.rs:143-146
 pub const FQH_E_SEP: c_int = 2;           // src/records.rs:157-160
@@ -188,6 +190,12 @@ extern "C" {
     pub fn fqh_gather_records(ctx: *mut fqh_ctx, d_buf: *const u8, len: u64, base_offset: u64,
                               d_index: *const fqh_idx_record, n: u64, d_flags: *const u8, mask: u8, want: u8,
                               d_out: *mut u8, out_cap: u64, n_selected: *mut u64, out_bytes: *mut u64) -> c_int;
+    // examples/alignment_count.rs:19-36: local_alignment_score(profile(query), record.seq(), gap_open, gap_extend) > threshold,
+    // for every record of the index at once; query is HOST memory (copied at the call), the outputs are nullable device pointers
+    pub fn fqh_align_scores(ctx: *mut fqh_ctx, d_buf: *const u8, len: u64, base_offset: u64,
+                            d_index: *const fqh_idx_record, n: u64, query: *const u8, query_len: u32,
+                            match_: i32, mismatch: i32, gap_open: i32, gap_extend: i32, threshold: i32,
+                            d_score: *mut i32, d_end: *mut u32, d_flags: *mut u8, d_count: *mut u64) -> c_int;
 
     // ---- benchmarks: kernel times of the last launch, the synthetic file of SURVEY 8(d), the bare streaming read
     pub fn fqh_last_timing(ctx: *mut fqh_ctx, out: *mut fqh_timing) -> c_int;

@@ -18,6 +18,8 @@
  *   validate_dna / validate_dnan    src/records.rs:19-33          fqh_stats (scalars 3,4), fqh_record_flags
  *   read lengths (sum of seq().len()) fuzz/fuzz_targets/fuzz_target_1.rs:16  fqh_len_hist
  *   Record::write (filter loops)    src/records.rs:93-96          fqh_gather_records
+ *   local_alignment_score per record examples/alignment_count.rs:19-36,  fqh_align_scores
+ *                                   src/lib.rs:78-91
  *   Buffer                          src/buffer.rs:1-112           fqh_stream_* (pinned ring)
  *   thread_reader                   src/thread_reader.rs:182-200  fqh_stream_* (copy stream)
  *   ... its copy box -> buffer      src/thread_reader.rs:90-97    removed: fqh_stream_submit_external (DMA from the host's memory)
@@ -446,6 +448,39 @@ fqh_status fqh_gather_records(fqh_ctx *ctx, const uint8_t *d_buf, uint64_t len, 
                               const fqh_idx_record *d_index, uint64_t n, const uint8_t *d_flags,
                               uint8_t mask, uint8_t want, uint8_t *d_out, uint64_t out_cap,
                               uint64_t *n_selected, uint64_t *out_bytes);
+
+/* ---- Per-record adapter alignment (examples/alignment_count.rs:19-36, src/lib.rs:78-91) -----------------------------------
+ * The score of a Smith-Waterman-Gotoh local alignment of every record's seq() against one query (the adapter), and the count of
+ * records that score above a threshold: what the crate's example computes in its parallel_each closure.  Same input contract
+ * as fqh_record_flags: d_buf / len / base_offset and the index d_index[0..n) of fqh_index_records.  The definition:
+ *   b = seq() of record r with one trailing '\r' trimmed (trim_winline, src/records.rs:66-73); q = query[0..query_len).
+ *   s(x, y) = match if the bytes are equal (case-sensitive), mismatch otherwise.  Bytes outside ACGTN are not special.
+ *   Gotoh local alignment, a gap of length k costs gap_open + (k-1)*gap_extend:
+ *     E[i][j] = max(E[i][j-1] - gap_extend, H[i][j-1] - gap_open)
+ *     F[i][j] = max(F[i-1][j] - gap_extend, H[i-1][j] - gap_open)
+ *     H[i][j] = max(0, H[i-1][j-1] + s(q_i, b_j), E[i][j], F[i][j])
+ *     boundaries (row 0 / column 0): H = 0, E = F = -infinity.
+ *   score = max H over all cells; an empty seq() scores 0.
+ *   end = the smallest 0-based index j into b such that some H[i][j] equals the score; UINT32_MAX when the score is 0.
+ * Reads of any length.  Argument ranges (FQH_E_ARG outside them) keep every value inside int16 (E, F >= -gap_open,
+ * H <= 64*127): 1 <= query_len <= FQH_ALIGN_MAX_QUERY, 1 <= match <= 127, -127 <= mismatch <= match,
+ * 0 <= gap_extend <= gap_open <= 127.
+ * The example's parameters are adapter AATGATACGGCGACCACCGAGATCTACACTCTTTCCCTACACGACGCTCTTCCGATCT, gap_open 8, gap_extend 1,
+ * threshold 10 (examples/alignment_count.rs:8-10,29-30) with match 1 / mismatch 0, our reading of parasailors'
+ * MatrixType::Identity.  That reading, and parasail's handling of bytes outside its matrix alphabet, are NOT verified against
+ * parasail: the recurrence above is the contract, and a caller who needs another reading passes its own numbers.
+ * Records with start < base_offset read their bytes from d_buf[-(base_offset - start) ..], which must be valid device memory
+ * (as for fqh_stats_launch_lead): a chunked caller keeps the record across a cut in front of the next chunk.
+ * Outputs (each may be NULL): d_score[r]; d_end[r]; d_flags[r] bit 2 (FQH_FLAG_ADAPTER) := score > threshold, the other bits
+ * untouched (so fqh_gather_records(mask 5, want 1) keeps the valid-DNA records without an adapter hit); *d_count is ADDED to
+ * with the number of records whose score > threshold.  The query is copied into the kernel's arguments at the call (the host
+ * buffer is free on return); the call is asynchronous on the context's stream (it only enqueues). */
+#define FQH_ALIGN_MAX_QUERY 64 /* longest query (adapter) in bytes */
+#define FQH_FLAG_ADAPTER 4u    /* bit of d_flags set by fqh_align_scores; bits 0-1 stay fqh_record_flags' */
+fqh_status fqh_align_scores(fqh_ctx *ctx, const uint8_t *d_buf, uint64_t len, uint64_t base_offset,
+                            const fqh_idx_record *d_index, uint64_t n, const uint8_t *query, uint32_t query_len,
+                            int32_t match, int32_t mismatch, int32_t gap_open, int32_t gap_extend, int32_t threshold,
+                            int32_t *d_score, uint32_t *d_end, uint8_t *d_flags, uint64_t *d_count);
 
 /* ---- Streaming ingest: the GPU counterpart of Buffer + thread_reader --------------------------
  * src/buffer.rs keeps one 68 KiB window and memmoves the partial trailing record to its front;
